@@ -16,6 +16,11 @@ ends after all of it. --shard contig: contiguous shards, each flow merged at its
 hash owner (OwnerExchange; TCBEE_BENCH_EXCHANGE=merge: the all-gather merge
 overlapped with the next parse, OverlappedMerge).
 
+A plain run sets up, warms up, times --steps steps and prints the line; --dump-outputs
+DIR writes what the last timed step computed. --full adds the check of that step
+against the oracle, the other configurations, the host end-to-end and replay legs and
+the CPU baseline.
+
 Prints ONE JSON line (rank 0). See DESIGN.md "Measurement".
 """
 from __future__ import annotations
@@ -165,7 +170,10 @@ def build_shard_trace(torch, n_global, world, rank, sizes, kind, n_flows, seed, 
 
 
 def run_device(torch, dist, rank, world, n, sizes, kind, n_flows, steps, warmup, seed,
-               multi=None, full_check=False, flowhash=False, vworld=0, warm=False):
+               multi=None, full_check=False, flowhash=False, vworld=0, warm=False,
+               validate=True, dump_dir=None):
+    """validate=False (a plain run): nothing is compared with the oracle after the
+    timed steps. dump_dir (rank 0): what the last timed step wrote, as .npy files."""
     import tcbee_amd
     stream = torch.cuda.current_stream().cuda_stream
     log(f"rank {rank}: building {n} frames ({sizes}, {n_flows} flows, "
@@ -323,13 +331,32 @@ def run_device(torch, dist, rank, world, n, sizes, kind, n_flows, steps, warmup,
     t1 = time.perf_counter()
     k1_ms, k1_launches = p.profile_read()
     elapsed = t1 - t0
-    log(f"rank {rank}: {steps} steps in {elapsed * 1e3:.1f} ms; validating")
+    log(f"rank {rank}: {steps} steps in {elapsed * 1e3:.1f} ms"
+        + ("; validating" if validate else ""))
     fx_ms = fx.exchange_ms() if fx is not None else None
     status = p.status()
 
-    # validation (untimed): counts, flow table, and a bit-exact sample vs the oracle
     last = slots[(count[0] - 1) % nbuf]
     nrec = int(last["n"].item())
+    if dump_dir and rank == 0:
+        dump_outputs(torch, dump_dir, last, nrec, seed, p.flows() if merged is None else None)
+
+    def release():
+        if ox is not None:
+            ox.owner.close()
+        p.close()
+        if merged is not None:
+            merged.close()
+        torch.cuda.empty_cache()
+
+    if not validate:
+        del d_arena, slots
+        release()
+        return elapsed, k1_ms / max(k1_launches, 1), nrec, {
+            "records": nrec, "status": status,
+            "host_issue_ms_per_step": round((t_issue - t0) / steps * 1e3, 4)}, n
+
+    # validation (untimed): counts, flow table, and a bit-exact sample vs the oracle
     if multi and p.flow_count() > xcap:
         raise RuntimeError(f"rank {rank}: {p.flow_count()} flows exceed the exchange cap {xcap}")
     if fx is not None:
@@ -389,14 +416,51 @@ def run_device(torch, dist, rank, world, n, sizes, kind, n_flows, steps, warmup,
     if multi:
         check.update(all_ranks_check(torch, dist, check, status, n, n_global if flowhash
                                      else world * n, flows, last["ctr"]))
-    if ox is not None:
-        ox.owner.close()
-    p.close()
-    if merged is not None:
-        merged.close()
     del d_arena, slots
-    torch.cuda.empty_cache()
+    release()
     return elapsed, k1_ms / max(k1_launches, 1), nrec, check, n
+
+
+DUMP_SAMPLE = 1 << 16  # rows of a larger output that --dump-outputs keeps
+
+
+def dump_outputs(torch, path, out, nrec, seed, flows):
+    """--dump-outputs: what the last timed step handed its caller (records, flow
+    hashes, flow ids, record count, the counters it added to since the first warm-up
+    step) and the flow table it left (a run with one table: no N>1 exchange), as
+    <path>/<name>.npy. Outputs of more than DUMP_SAMPLE rows are sampled: the first
+    and last row and DUMP_SAMPLE rows drawn from --seed (the same rows in every run
+    with the same arguments; their indices are written too). Bytes as float32, 32- and
+    64-bit integers as float64 (exact below 2^53)."""
+    os.makedirs(path, exist_ok=True)
+
+    def rows(n):
+        if n <= DUMP_SAMPLE:
+            return np.arange(n, dtype=np.int64)
+        rng = np.random.default_rng(seed)
+        return np.unique(np.concatenate([[0, n - 1], rng.integers(0, n, DUMP_SAMPLE)]))
+
+    idx = rows(nrec)
+    d_idx = torch.from_numpy(idx).cuda()
+    rec = out["rec"][:nrec * 74].view(nrec, 74)[d_idx].cpu().numpy()
+    arrays = {"record_index": idx.astype(np.float64), "records": rec.astype(np.float32),
+              "flow_hash": out["hash"][:nrec][d_idx].cpu().numpy().view(np.uint32)
+              .astype(np.float64),
+              "flow_id": out["id"][:nrec][d_idx].cpu().numpy().view(np.uint32).astype(np.float64),
+              "n_records": np.array([nrec], np.float64),
+              "counters": out["ctr"].cpu().numpy().astype(np.float64)}
+    if flows is not None:
+        fidx = rows(len(flows))
+        arrays["flow_index"] = fidx.astype(np.float64)
+        arrays["flow_table"] = (np.ascontiguousarray(flows[fidx]).view(np.uint8)
+                                .reshape(len(fidx), flows.dtype.itemsize).astype(np.float32))
+    else:
+        log("outputs: no flow table written (with the N>1 exchange the global table is "
+            "assembled only by --full's check, not by a timed step)")
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"outputs written to {path}: "
+        + ", ".join(f"{k}{list(a.shape)}" for k, a in arrays.items()))
 
 
 def all_ranks_check(torch, dist, check, status, n_local, n_global, flows, ctr):
@@ -774,6 +838,19 @@ def host_e2e(sizes, kind, n_flows, seed, n=20_000_000, reps=9, threads=None):
                 ("pipe_whole", 0, "registered"))
     pipes, ts = {}, {}
     rec_out, id_out = np.empty((n, 74), np.uint8), np.empty(n, np.uint32)
+    # A host whose HIP runtime refuses to page-lock memory the process already has
+    # (asked of the runtime alone, tests/hostreg.py): the pair is allocated page-locked
+    # instead and the "registered" pipes borrow it — no hipHostRegister by the pipe,
+    # and every leg's "output" says so. Any refusal by a pipe is an error either way.
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from hostreg import host_register_error
+    borrowed = host_register_error() != 0
+    if borrowed:
+        import torch
+        rec_out = torch.empty((n, 74), dtype=torch.uint8, pin_memory=True).numpy()
+        id_out = torch.empty(n, dtype=torch.int32, pin_memory=True).numpy().view(np.uint32)
+        out["outputs"] = ("allocated page-locked: hipHostRegister returns hipError "
+                          f"{host_register_error()} on this host")
     ref = None
     identical = True
     try:
@@ -814,7 +891,8 @@ def host_e2e(sizes, kind, n_flows, seed, n=20_000_000, reps=9, threads=None):
         how = pipes[name].output_mode
         out[name] = {"mpkts": round(n / el / 1e6, 1), "s": round(el, 4), "records": last[name].n,
                      "h2d_bytes": h2d, "h2d_GBs": round(h2d / el / 1e9, 1),
-                     "output": ("registered (direct D2H)" if how == "registered"
+                     "output": (("page-locked allocation borrowed (direct D2H)" if borrowed
+                                 else "registered (direct D2H)") if how == "registered"
                                 else "staged + copy-out")
                      + (" — chosen by calibration" if mode == "auto" else ""),
                      "best_mpkts": round(n / min(ts[name]) / 1e6, 1)}
@@ -947,7 +1025,18 @@ def main():
                          "shards, FlowHashExchange); 125M = BASELINE.json's 1B at N=8. "
                          "Smaller only to rehearse N ranks on one GPU")
     ap.add_argument("--c4-steps", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run: check its last step against the oracle "
+                         "(every record at N=1, --sample-check: a sample), run the other "
+                         "configurations, the host end-to-end and replay legs (--no-extra "
+                         "skips them) and the CPU baseline (--no-cpu skips it). A plain run "
+                         "times the headline steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy "
+                         "(float32/float64; large outputs as a fixed sample drawn from --seed)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu = args.no_extra = True
     if args.config4:
         args.frames, args.flows, args.sizes = 125_000_000, 1_000_000, "imix"
         args.shard = args.shard or "flowhash"
@@ -986,7 +1075,7 @@ def main():
         torch, dist, rank, world, args.frames, args.sizes, kind, args.flows, args.steps,
         args.warmup, args.seed, multi=world > 1 or force_merge,
         full_check=not args.sample_check, flowhash=args.shard == "flowhash",
-        vworld=args.virtual_world)
+        vworld=args.virtual_world, validate=args.full, dump_dir=args.dump_outputs)
     if world > 1:
         elapsed = max_over_ranks(torch, dist, elapsed)
     c4 = None

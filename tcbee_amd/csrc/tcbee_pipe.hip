@@ -245,6 +245,7 @@ hipError_t register_range(void* ptr, uint64_t bytes) {
   }
   const hipError_t e = hipHostRegister(ptr, bytes, hipHostRegisterDefault);
   if (e == hipSuccess) g_regs.push_back({b, bytes, 1});
+  else (void)hipGetLastError();  // (reported here; must not surface in a later call)
   return e;
 }
 

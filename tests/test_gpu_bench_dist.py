@@ -62,7 +62,7 @@ def check_leg(chk: dict, world: int, full: bool = True):
 
 def test_bench_world2_flowhash_and_config4_leg(gpu):
     out = run_bench_world(2, ["--frames", "4000000", "--steps", "2", "--warmup", "1",
-                              "--c4-frames", "6000000", "--c4-steps", "2"])
+                              "--c4-frames", "6000000", "--c4-steps", "2", "--full"])
     assert out["n_gpus"] == 2 and out["scaling"] == "weak"
     assert out["dist"] == {"backend": "gloo", "world_size": 2}
     assert out["config"]["shard"] == "flowhash" and out["config"]["parallelism"] == "shard2"
@@ -89,7 +89,8 @@ def test_bench_world4_flowhash_and_config4_leg(gpu):
     """World 4 (four ranks on device 0 over gloo): both legs bit-exact on every rank,
     the exchange capacity sized from the RSS table's flows per rank."""
     out = run_bench_world(4, ["--frames", "2000000", "--steps", "2", "--warmup", "1",
-                              "--c4-frames", "3000000", "--c4-steps", "2", "--no-cpu"],
+                              "--c4-frames", "3000000", "--c4-steps", "2", "--full",
+                              "--no-cpu"],
                           timeout=600)
     assert out["n_gpus"] == 4 and out["dist"] == {"backend": "gloo", "world_size": 4}
     chk = out["check"]
@@ -129,7 +130,7 @@ def test_bench_world1_over_rccl(gpu, shard):
     one-rank RCCL communicator — RCCL refuses two ranks on one GPU, so this is the
     most of the collective path a one-GPU box can run; every record bit-exact."""
     out = run_bench_world(1, ["--frames", "4000000", "--steps", "2", "--warmup", "1",
-                              "--no-cpu", "--no-extra", "--shard", shard],
+                              "--full", "--no-cpu", "--no-extra", "--shard", shard],
                           TCBEE_DIST_BACKEND="nccl", TCBEE_BENCH_FORCE_MERGE="1")
     assert out["dist"] == {"backend": "nccl", "world_size": 1}
     assert out["config"]["shard"] == shard
@@ -144,7 +145,7 @@ def test_k1_beside_a_second_process(gpu):
     polled for a bounded time, then recounted and published for the other waiters.
     With the old poll-count bound this took ~290x the K1 of one process alone
     (profiles/r05_lookback_contention.log); now ~2.7x. Bound: 15x."""
-    args = ["--frames", "10000000", "--steps", "30", "--warmup", "3", "--no-cpu",
+    args = ["--frames", "10000000", "--steps", "30", "--warmup", "3", "--full", "--no-cpu",
             "--no-extra", "--sample-check"]
     env = dict(os.environ, PYTHONUNBUFFERED="1")
     r = subprocess.run([sys.executable, "bench.py"] + args, cwd=ROOT, env=env,

@@ -12,6 +12,7 @@ import pytest
 import tcbee_amd
 from tcbee_amd import host
 from tcbee_amd.pipeline import Pipeline, replay_pcap
+from hostreg import host_register_error
 from tracegen import mixed_trace
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -128,8 +129,29 @@ def test_pipeline_sink_callback_and_out_cap(gpu, oracle):
         assert np.array_equal(small, rec[:100])
 
 
+def _output_pair(n: int, record_property):
+    """Zeroed records [n, 74] and ids [n] for register_output. Where the HIP runtime
+    page-locks existing memory (hostreg.host_register_error() == 0, asked of the runtime
+    alone before any pipe exists): pageable arrays, which the pipe page-locks, shares
+    and releases itself, and a refusal by the pipe fails the test. Where the runtime
+    refuses: arrays allocated page-locked, which the pipe borrows as a caller's own
+    page-locking (then the pipe's hipHostRegister / registry path does not run). The
+    path taken is recorded with the test (property "output_arrays") and printed."""
+    err = host_register_error()
+    how = ("pageable, page-locked by the pipe" if err == 0 else
+           f"allocated page-locked, borrowed (hipHostRegister returns {err} on this host)")
+    record_property("output_arrays", how)
+    print("output arrays:", how)
+    if err == 0:
+        return np.zeros((n, 74), np.uint8), np.zeros(n, np.uint32)
+    import torch
+    out = torch.zeros((n, 74), dtype=torch.uint8, pin_memory=True).numpy()
+    ids = torch.zeros(n, dtype=torch.int32, pin_memory=True).numpy().view(np.uint32)
+    return out, ids
+
+
 @pytest.mark.parametrize("window", [64, 0])
-def test_pipeline_registered_output(gpu, oracle, window):
+def test_pipeline_registered_output(gpu, oracle, window, record_property):
     """the caller's arrays registered once (tcbee_pipe_register_output):
     chunks DMA straight into them. Records / ids / counters equal the oracle; the
     sink sees the same records (pointers into the caller's arrays); flow ids continue
@@ -139,8 +161,7 @@ def test_pipeline_registered_output(gpu, oracle, window):
     t = mixed_trace(50_000, seed=61, n_flows=400)
     rec, fh, fi, ctr, table = oracle.parse(t)
     n = len(rec)
-    out = np.zeros((n + 50, 74), np.uint8)
-    ids = np.zeros(n + 50, np.uint32)
+    out, ids = _output_pair(n + 50, record_property)
     with Pipeline(device=0, chunk_frames=4096, window=window, depth=3, threads=4,
                   max_flows=1 << 12) as p:
         p.register_output(out, ids)
@@ -173,7 +194,7 @@ def test_pipeline_registered_output(gpu, oracle, window):
             p.register_output(np.zeros((10, 70), np.uint8))
 
 
-def test_pipeline_shared_registration_and_calibration(gpu, oracle):
+def test_pipeline_shared_registration_and_calibration(gpu, oracle, record_property):
     """Round 5: two pipes share ONE registered output pair
     (the second borrows the first's page-locking, and releasing the borrower leaves it
     registered for the owner); calibrate_output times direct D2H against staging on
@@ -182,8 +203,7 @@ def test_pipeline_shared_registration_and_calibration(gpu, oracle):
     t = mixed_trace(60_000, seed=62, n_flows=500)
     want = oracle.parse(t)
     n = len(want[0])
-    out = np.zeros((n, 74), np.uint8)
-    ids = np.zeros(n, np.uint32)
+    out, ids = _output_pair(n, record_property)
     with Pipeline(device=0, chunk_frames=4096, window=64, depth=3, threads=4,
                   max_flows=1 << 12) as owner:
         owner.register_output(out, ids)
@@ -233,6 +253,10 @@ def test_pipeline_registration_refcounted(gpu, oracle):
     when the borrower releases it. (2) A borrower asking for more than the owner
     locked (a larger cap over the same arrays) is refused, not sent past the pinned
     range. (3) A caller's own hipHostRegister is borrowed and never unregistered."""
+    err = host_register_error()  # (the runtime alone, before any pipe exists)
+    if err:
+        pytest.skip("needs a host whose HIP runtime page-locks existing memory: "
+                    f"hipHostRegister of an 8 MiB anonymous mapping returns hipError {err}")
     t = mixed_trace(40_000, seed=63, n_flows=300)
     want = oracle.parse(t)
     n = len(want[0])
@@ -271,6 +295,32 @@ def test_pipeline_registration_refcounted(gpu, oracle):
         assert _hip_host_registered(out)  # and left to the caller
     finally:
         assert int(cr.cudaHostUnregister(out.ctypes.data)) == 0
+
+
+def test_pipeline_refused_registration_leaves_no_error(gpu, oracle):
+    """A refused register_output (EINVAL) leaves nothing behind: the pipe stays
+    unregistered and usable, and a pipe created afterwards runs (a HIP error left by
+    the refusal used to be reported by the next launch's error query, so that
+    tcbee_pipe_create failed with EDEVICE). The refusal: a range that covers more
+    than another pipe page-locked; on a host whose runtime refuses hipHostRegister
+    (hostreg), the runtime's own refusal of pageable arrays."""
+    t = mixed_trace(20_000, seed=64, n_flows=100)
+    want = oracle.parse(t)
+    n = len(want[0])
+    out = np.zeros((n, 74), np.uint8)
+    ids = np.zeros(n, np.uint32)
+    kw = dict(device=0, chunk_frames=4096, window=64, depth=3, threads=2, max_flows=1 << 12)
+    with Pipeline(**kw) as small, Pipeline(**kw) as p:
+        if host_register_error() == 0:
+            small.register_output(out[:n // 2], ids[:n // 2])
+        with pytest.raises(tcbee_amd.TcbeeError) as ei:
+            p.register_output(out, ids)
+        assert ei.value.code == tcbee_amd._lib.EINVAL
+        assert p.output_mode == "staged"
+        check_same(p.run(t, out_rec=out, out_id=ids), want, p.flows())
+    with Pipeline(**kw) as q:
+        out[:] = 0
+        check_same(q.run(t, out_rec=out, out_id=ids), want, q.flows())
 
 
 def test_pipeline_empty_and_tiny(gpu, oracle):

@@ -4,7 +4,7 @@
 # each checking its last step's records, ids and table in full against the oracle.
 set -u
 mkdir -p gpurun_out
-A="--frames ${FRAMES:-20000000} --steps ${STEPS:-60} --warmup 2 --no-cpu --no-extra"
+A="--frames ${FRAMES:-20000000} --steps ${STEPS:-60} --warmup 2 --full --no-cpu --no-extra"
 for i in 1 2; do
   timeout -k 10 400 python bench.py $A > gpurun_out/cc_$i.json 2> gpurun_out/cc_$i.err &
   eval p$i=$!

@@ -33,16 +33,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "gpurun_out")
 PROF = os.path.join(ROOT, "profiles")
 
-LEGS = {"c3": ("config 3: 100M IMIX frames, 10k flows", "", "--no-extra --no-cpu"),
+LEGS = {"c3": ("config 3: 100M IMIX frames, 10k flows", "", "--full --no-extra --no-cpu"),
         "c4v8": ("config 4, one GPU's flow-hash share at N=8: ~125M frames, ~125k flows",
                  "--config4 --virtual-world 8",
-                 "--config4 --virtual-world 8 --steps 5 --warmup 1 --no-cpu --no-extra"),
+                 "--full --config4 --virtual-world 8 --steps 5 --warmup 1 --no-cpu --no-extra"),
         "c4": ("config 4, the whole 1M-flow trace on one GPU: 125M IMIX frames",
-               "--config4", "--config4 --shard contig --steps 5 --warmup 1 --no-cpu --no-extra"),
+               "--config4", "--full --config4 --shard contig --steps 5 --warmup 1 --no-cpu --no-extra"),
         "v6": ("config 3 over IPv6/TCP: 100M IMIX6 frames, 10k flows", "--sizes imix6",
-               "--sizes imix6 --no-extra --no-cpu"),
+               "--full --sizes imix6 --no-extra --no-cpu"),
         "c2": ("config 2: 1M 64-B frames, 1 flow", "--frames 1000000 --sizes 64 --flows 1",
-               "--frames 1000000 --sizes 64 --flows 1 --steps 200 --warmup 20 --no-extra --no-cpu")}
+               "--full --frames 1000000 --sizes 64 --flows 1 --steps 200 --warmup 20 --no-extra --no-cpu")}
 
 
 def pmc_values(path, kernel_sub):
