@@ -77,6 +77,8 @@ extern "C" {
 
 /* ---- cfg flags ------------------------------------------------------------ */
 #define TCBEE_F_NO_FLOWS     0x1u /* skip flow classification (hash/id/table) */
+#define TCBEE_F_DECODE       0x2u /* decoded parse: see tcbee_cfg                 */
+#define TCBEE_DECODE_MAX_HDR 128  /* decoded parse: the TCP header ends by this byte */
 
 typedef struct tcbee_ctx tcbee_ctx;
 
@@ -84,7 +86,36 @@ typedef struct tcbee_ctx tcbee_ctx;
  * filter_port: the FILTER_PORT global (tcbee-ebpf/src/main.rs:30-31), set by
  *   EbpfLoader::set_global (tcbee/src/eBPF/ebpf_runner.rs:79-84). Host order;
  *   0 = no filter; otherwise a frame is kept only if sport or dport equals it
- *   (xdp.rs:89-92, tc.rs:72-77). */
+ *   (xdp.rs:89-92, tc.rs:72-77).
+ * flags: TCBEE_F_*; any other bit is TCBEE_EINVAL.
+ *
+ * TCBEE_F_DECODE selects the decoded parse for the batch (this project's own rules,
+ * not the reference's: the default mode reads TCP at frame byte 34 / 54 whatever
+ * the frame says and writes six zero flag bytes). caplen is clamped to the arena
+ * as always, multi-byte fields are big-endian, and "reject" is what a non-TCP
+ * frame gets: no record, no key, no counter change.
+ *   1. Reject if caplen < 14. et = bytes 12..13, l3 = 14.
+ *   2. VLAN: at most twice while et is 0x8100 or 0x88A8: reject if caplen < l3 + 4;
+ *      et = bytes l3+2..l3+3; l3 += 4. A third tag is rejected.
+ *   3. et 0x0800: reject if caplen < l3 + 20, if the version nibble is not 4, if
+ *      ihl (low nibble of byte l3) < 5, if byte l3+9 != 6, or if (bytes l3+6..7 &
+ *      0x1FFF) != 0 (a non-first fragment). l4 = l3 + 4 ihl; addresses at l3+12
+ *      and l3+16.
+ *   4. et 0x86DD: reject if caplen < l3 + 40. nh = byte l3+6, l4 = l3 + 40,
+ *      addresses at l3+8 and l3+24. At most 4 extension headers are walked:
+ *      nh 0, 43, 60: reject if caplen < l4 + 8; nh = byte l4, l4 += 8 (byte[l4+1] + 1).
+ *      nh 44: reject if caplen < l4 + 8 or (bytes l4+2..3 & 0xFFF8) != 0;
+ *      nh = byte l4, l4 += 8. (Bytes are read before l4 advances.) Then reject
+ *      unless nh == 6: a fifth extension header, ESP, AH, ... are rejected.
+ *   5. Any other et: reject.
+ *   6. TCP at l4: reject if l4 + 20 > caplen, if l4 + 20 > TCBEE_DECODE_MAX_HDR
+ *      (no frame byte at or past 128 is ever read), or if the data offset
+ *      (byte l4+12 >> 4) < 5. Ports, seq, ack, window and checksum are the default
+ *      mode's fields, relative to l4; filter_port applies as always.
+ *   7. The record and the IpTuple key have the default mode's layout; record bytes
+ *      62..67 (urg, ack, psh, rst, syn, fin) are bits 5, 4, 3, 2, 1, 0 of byte
+ *      l4+13, each 0 or 1. Hash, ids, flow table, counters, out_cap drops and the
+ *      TCBEE_EX_* outputs are unchanged; a context may mix batches of both modes. */
 typedef struct tcbee_cfg {
     uint16_t filter_port;
     uint8_t  direction;      /* TCBEE_DIR_*                               */
@@ -469,7 +500,9 @@ int tcbee_gen_rss_load_range_device(uint64_t first_frame, uint64_t n_frames, int
  * original caplen — the record path never reads past byte 74 of a frame, so
  * outputs are identical, and PCIe carries ~window+12 bytes per frame.
  * window == 64: frame bytes [12, 76) (no record field reads the MAC addresses),
- * one whole 64-B staging line per frame — the fastest gather. */
+ * one whole 64-B staging line per frame — the fastest gather.
+ * With TCBEE_F_DECODE a batch may read any frame byte below TCBEE_DECODE_MAX_HDR,
+ * so tcbee_pipe_run returns TCBEE_EINVAL unless window == 0 or window >= 128. */
 typedef struct tcbee_pipe tcbee_pipe;
 typedef struct tcbee_pipe_cfg {
     uint64_t chunk_frames;  /* frames per chunk (0 = 1<<20)                     */

@@ -6,8 +6,8 @@ classification of raw frames, emitting TCBee's 74-byte ``*.tcp`` records
 ``tcbee_amd/lib/libtcbee_amd.so``, reached through the C ABI of
 ``include/tcbee_amd.h``.
 """
-from ._lib import (DIR_EGRESS, DIR_INGRESS, EXPORTED, F_NO_FLOWS, KEY_BYTES, LIB_PATH,
-                   RECORD_BYTES, TcbeeError, device_count, lib)
+from ._lib import (DIR_EGRESS, DIR_INGRESS, EXPORTED, F_DECODE, F_NO_FLOWS, KEY_BYTES,
+                   LIB_PATH, RECORD_BYTES, TcbeeError, device_count, lib)
 from .parser import (FLOW_DTYPE, PacketParser, ParseResult, flow_hash64, gen_frames_device,
                      gen_frames_index_device, gen_rss_load_device, gen_shard_index_device,
                      gen_shard_scratch_words)
@@ -15,7 +15,7 @@ from .trace import (RSS_BUCKETS, Trace, rss_flows_per_rank, rss_table, splitmix6
                     synth_index, synth_trace)
 
 __all__ = [
-    "DIR_EGRESS", "DIR_INGRESS", "EXPORTED", "F_NO_FLOWS", "KEY_BYTES", "LIB_PATH",
+    "DIR_EGRESS", "DIR_INGRESS", "EXPORTED", "F_DECODE", "F_NO_FLOWS", "KEY_BYTES", "LIB_PATH",
     "RECORD_BYTES", "TcbeeError", "device_count", "lib", "FLOW_DTYPE", "PacketParser",
     "ParseResult", "flow_hash64", "gen_frames_device", "gen_frames_index_device",
     "gen_rss_load_device", "gen_shard_index_device", "gen_shard_scratch_words", "RSS_BUCKETS",

@@ -36,6 +36,7 @@ KEY_BYTES = 40
 DIR_INGRESS = 0
 DIR_EGRESS = 1
 F_NO_FLOWS = 0x1
+F_DECODE = 0x2
 
 OK = 0
 EINVAL = -1

@@ -542,12 +542,14 @@ int tcbee_parse_batch_device_ex(tcbee_ctx* c, const tcbee_frames* in, const tcbe
   }
   if (out_frame && in->n > 0xFFFFFFFFull) return TCBEE_EINVAL;  // u32 frame indices
   if (cfg->direction > 1) return TCBEE_EINVAL;
+  if (cfg->flags & ~(TCBEE_F_NO_FLOWS | TCBEE_F_DECODE)) return TCBEE_EINVAL;
   if (in->n > c->max_frames) return TCBEE_ECAPACITY;
   if (in->n && (!in->arena || !in->offset || !in->caplen || !in->ts_ns)) return TCBEE_EINVAL;
   if (out_cap && !out_rec74) return TCBEE_EINVAL;
   if ((in->arena && !aligned16(in->arena)) || (out_rec74 && !aligned16(out_rec74)))
     return TCBEE_EINVAL;
   const bool flows = (cfg->flags & TCBEE_F_NO_FLOWS) == 0;
+  const bool decode = (cfg->flags & TCBEE_F_DECODE) != 0;
   hipStream_t s;
   TRY_HIP(ctx_stream(c, stream, s));  // (sets c->device current)
   if (async && c->nslot < 2) {
@@ -630,7 +632,7 @@ int tcbee_parse_batch_device_ex(tcbee_ctx* c, const tcbee_frames* in, const tcbe
     a.out_frame = out_frame;
     const bool timed = c->profiling && c->ev_used < kMaxProfiled;
     if (timed) TRY_HIP(hipEventRecord(c->ev[2 * c->ev_used], s));
-    TRY_HIP(launch_parse(a, fpl, flows, s));
+    TRY_HIP(launch_parse(a, fpl, flows, decode, s));
     if (timed) {
       TRY_HIP(hipEventRecord(c->ev[2 * c->ev_used + 1], s));
       ++c->ev_used;

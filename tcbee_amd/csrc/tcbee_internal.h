@@ -157,7 +157,8 @@ struct RankArgs {
 
 // Launchers (tcbee_kernels.hip). All asynchronous on `s`.
 hipError_t launch_table_init(FlowTable t, hipStream_t s);
-hipError_t launch_parse(const ParseArgs& a, int fpl, bool flows, hipStream_t s);
+// decode: the decoded parse (TCBEE_F_DECODE) instead of the fixed-offset one
+hipError_t launch_parse(const ParseArgs& a, int fpl, bool flows, bool decode, hipStream_t s);
 hipError_t launch_rank(const RankArgs& r, hipStream_t s);
 #if TCBEE_VARIANTS
 // test hook: one lane holds `s` until *flag_dev == expect (a page-locked coherent host

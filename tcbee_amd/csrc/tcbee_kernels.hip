@@ -128,6 +128,60 @@ __device__ __forceinline__ void load_windows(const uint8_t* __restrict__ arena, 
   }
 }
 
+// u[j] = frame bytes [4j, 4j+4) of a window whose frame starts at byte s of w
+__device__ __forceinline__ void window_dwords(const uint32_t (&w)[24], uint32_t s, uint32_t (&u)[19]) {
+  const uint32_t q = s >> 2, r = s & 3u;
+  const uint32_t m1 = 0u - (q & 1u), m2 = 0u - ((q >> 1) & 1u);
+  uint32_t t[23];
+#pragma unroll
+  for (int j = 0; j < 23; ++j) t[j] = (w[j] & ~m1) | (w[j + 1] & m1);
+  uint32_t v2[21];
+#pragma unroll
+  for (int j = 0; j < 21; ++j) v2[j] = (t[j] & ~m2) | (t[j + 2] & m2);
+#pragma unroll
+  for (int j = 0; j < 19; ++j) u[j] = align_bytes(v2[j + 1], v2[j], r);
+}
+
+// The 74-B record (tcp_packet_trace bincode + marker, xdp.rs:94-112 / :168-186) and
+// the IpTuple key (xdp.rs:116-127 / :189-195: v4 address = 12 zero bytes + wire
+// bytes) of an accepted frame. Addresses are the wire bytes as LE words; fl = the six
+// flag bytes urg, ack, psh, rst, syn, fin (0 or 1 each).
+__device__ __forceinline__ void make_record(uint64_t ts, bool v4, uint32_t sa4, uint32_t da4,
+                                            const uint32_t (&sa6)[4], const uint32_t (&da6)[4],
+                                            uint32_t sport, uint32_t dport, uint32_t seq,
+                                            uint32_t ack, uint32_t window, const uint32_t (&fl)[6],
+                                            uint32_t check, uint32_t (&R)[19], uint64_t (&K)[5]) {
+  const bool v6 = !v4;
+  R[0] = (uint32_t)ts;
+  R[1] = (uint32_t)(ts >> 32);
+  R[2] = v4 ? bswap32(sa4) : 0u;  // saddr.to_be()
+  R[3] = v4 ? bswap32(da4) : 0u;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    R[4 + j] = v6 ? sa6[j] : 0u;
+    R[8 + j] = v6 ? da6[j] : 0u;
+  }
+  R[12] = sport | (dport << 16);
+  R[13] = seq;
+  R[14] = ack;
+  R[15] = window | (fl[0] << 16) | (fl[1] << 24);
+  R[16] = fl[2] | (fl[3] << 8) | (fl[4] << 16) | (fl[5] << 24);
+  R[17] = check | 0xFFFF0000u;  // checksum + first half of FF FF FF FF
+  R[18] = 0x0000FFFFu;
+  if (v4) {
+    K[0] = 0;
+    K[1] = (uint64_t)sa4 << 32;
+    K[2] = 0;
+    K[3] = (uint64_t)da4 << 32;
+  } else {
+    K[0] = (uint64_t)sa6[0] | ((uint64_t)sa6[1] << 32);
+    K[1] = (uint64_t)sa6[2] | ((uint64_t)sa6[3] << 32);
+    K[2] = (uint64_t)da6[0] | ((uint64_t)da6[1] << 32);
+    K[3] = (uint64_t)da6[2] | ((uint64_t)da6[3] << 32);
+  }
+  K[4] = (uint64_t)sport | ((uint64_t)dport << 16) | ((uint64_t)kTcpProtocol << 32);
+}
+
 __device__ __forceinline__ bool parse_window(const uint8_t* __restrict__ arena, uint64_t arena_len,
                                              uint64_t off, uint32_t caplen, uint64_t ts,
                                              uint32_t filter_port, uint32_t (&w)[24],
@@ -244,6 +298,144 @@ __device__ __forceinline__ bool parse_window(const uint8_t* __restrict__ arena, 
 }
 
 // ---------------------------------------------------------------------------
+// The decoded parse (TCBEE_F_DECODE): the frame's own VLAN tags, IHL and IPv6
+// extension headers place the IP and TCP headers, and the six flag bytes are the
+// TCP flag bits. Accept rules: include/tcbee_amd.h (tcbee_cfg) and DESIGN.md
+// "Decoded mode". Everything after the parse is the fixed mode's.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kEthertypeVlan = 0x8100, kEthertypeQinQ = 0x88A8;
+constexpr uint32_t kDecodeMaxHdr = TCBEE_DECODE_MAX_HDR;
+constexpr uint32_t kNhHopByHop = 0, kNhRouting = 43, kNhFragment = 44, kNhDestOpts = 60;
+
+// out = arena bytes [a, a + 4 NDW) at any alignment: the 16-B chunks that hold them
+// (bounds-checked, all issued before the first use), a dword shift by two select
+// stages and a byte align by a & 3 — parse_window's normalisation with the shift
+// taken from the address instead of the window's start.
+template <int NDW>
+__device__ __forceinline__ void fetch_bytes(const uint8_t* __restrict__ arena, uint64_t arena_len,
+                                            uint64_t a, uint32_t (&out)[NDW]) {
+  constexpr int NCH = (4 * NDW + 30) / 16;  // chunks a run of 4 NDW bytes can touch
+  static_assert(4 * NCH >= NDW + 4, "the select stages read c[NDW + 3]");
+  const uint64_t abase = a & ~15ull;
+  const uint32_t s = (uint32_t)(a & 15u), end = s + 4u * NDW;
+  uint32_t c[4 * NCH];
+#pragma unroll
+  for (int k = 0; k < NCH; ++k) {
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if ((uint32_t)(16 * k) < end) v = load_chunk(arena, arena_len, abase + 16u * k);
+    c[4 * k + 0] = v.x; c[4 * k + 1] = v.y; c[4 * k + 2] = v.z; c[4 * k + 3] = v.w;
+  }
+  const uint32_t q = s >> 2, r = s & 3u;
+  const uint32_t m1 = 0u - (q & 1u), m2 = 0u - ((q >> 1) & 1u);
+  uint32_t t[NDW + 3];
+#pragma unroll
+  for (int j = 0; j < NDW + 3; ++j) t[j] = (c[j] & ~m1) | (c[j + 1] & m1);
+  uint32_t v2[NDW + 1];
+#pragma unroll
+  for (int j = 0; j < NDW + 1; ++j) v2[j] = (t[j] & ~m2) | (t[j + 2] & m2);
+#pragma unroll
+  for (int j = 0; j < NDW; ++j) out[j] = align_bytes(v2[j + 1], v2[j], r);
+}
+
+// Stage 1 reads everything from the window the fixed mode loads (frame bytes
+// [12, 52)): the up to three ethertype candidates (bytes 12, 16, 20), and — moved
+// down by the tag count with mask selects — the IPv4 header or the IPv6 next-header
+// byte (l3 + 20 <= 42). An untagged IPv4 frame with IHL 5 ("standard") has its TCP
+// header in the window too and is finished from registers. Stage 2 runs only in a
+// wave where some lane's frame is not standard (one ballot): such a lane fetches the
+// 20 TCP bytes at its own l4 and, for IPv6, the 32 address bytes — independent
+// loads, issued together — after the serial walk over at most 4 extension headers
+// (one 4-B fetch each). No frame byte at or past kDecodeMaxHdr is ever used.
+__device__ __forceinline__ bool parse_decoded(const uint8_t* __restrict__ arena, uint64_t arena_len,
+                                              uint64_t off, uint32_t caplen, uint64_t ts,
+                                              uint32_t filter_port, const uint32_t (&w)[24],
+                                              uint32_t (&R)[19], uint64_t (&K)[5]) {
+  uint32_t u[19];
+  window_dwords(w, (uint32_t)(off & 15u), u);
+  auto is_vlan = [](uint32_t e) { return e == kEthertypeVlan || e == kEthertypeQinQ; };
+  const uint32_t et0 = bswap16(u[3] & 0xFFFFu), et1 = bswap16(u[4] & 0xFFFFu),
+                 et2 = bswap16(u[5] & 0xFFFFu);  // bytes 12..13, 16..17, 20..21
+  const uint32_t tags = is_vlan(et0) ? (is_vlan(et1) ? 2u : 1u) : 0u;
+  // (a third tag leaves a VLAN ethertype here: neither IPv4 nor IPv6, rejected)
+  const uint32_t et = tags == 0 ? et0 : tags == 1 ? et1 : et2;
+  const uint32_t l3 = kEthHdrLen + 4u * tags;
+  // h[j] = frame bytes [4 (j + tags), +4): the IP header's dwords where an untagged
+  // frame has them, so every field below sits at a fixed place
+  const uint32_t k1 = 0u - (tags & 1u), k2 = 0u - (tags >> 1);
+  uint32_t h[9];
+#pragma unroll
+  for (int j = 3; j < 9; ++j) h[j] = (u[j] & ~(k1 | k2)) | (u[j + 1] & k1) | (u[j + 2] & k2);
+  const bool v4 = et == kEthertypeIPv4, v6 = et == kEthertypeIPv6;
+  const uint32_t vihl = (h[3] >> 16) & 0xFFu, ihl = vihl & 15u;     // ip[0]
+  const uint32_t fragoff = bswap16(h[5] & 0xFFFFu) & 0x1FFFu;       // ip[6..7]
+  // (caplen >= l3 is the caplen >= 14 and the per-tag caplen >= l3 + 4 checks)
+  bool ok = caplen >= l3 &&
+            ((v4 && caplen >= l3 + kIpHdrLen && (vihl >> 4) == 4 && ihl >= 5 &&
+              (h[5] >> 24) == kTcpProtocol && fragoff == 0) ||  // ip[9]
+             (v6 && caplen >= l3 + kIp6HdrLen));
+  uint32_t nh = h[5] & 0xFFu;  // ip6[6]
+  uint32_t l4 = v4 ? l3 + 4u * ihl : l3 + kIp6HdrLen;
+  const uint32_t sa4 = align_bytes(h[7], h[6], 2);  // ip[12..15] as LE word
+  const uint32_t da4 = align_bytes(h[8], h[7], 2);  // ip[16..19]
+  uint32_t sa6[4] = {0u, 0u, 0u, 0u}, da6[4] = {0u, 0u, 0u, 0u};
+  // T = frame bytes [l4, l4 + 20); of a standard frame: bytes 34..51 of the window
+  uint32_t T[5];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) T[j] = align_bytes(u[9 + j], u[8 + j], 2);
+  T[4] = u[12] >> 16;
+  const bool stage2 = ok && !(v4 && l4 == kEthHdrLen + kIpHdrLen);
+  if (__any(stage2)) {
+    if (stage2) {
+      uint32_t A[8];
+      if (v6) {
+        fetch_bytes<8>(arena, arena_len, off + l3 + 8, A);  // ip6[8..39]
+        for (int e = 0; e < 4 && ok; ++e) {
+          if (nh != kNhHopByHop && nh != kNhRouting && nh != kNhDestOpts && nh != kNhFragment) break;
+          // (an extension header that ends past kDecodeMaxHdr - 20 leaves no room
+          //  for the TCP header below it: rejected here, before its bytes are read)
+          if (caplen < l4 + 8 || l4 + 8 > kDecodeMaxHdr) {
+            ok = false;
+            break;
+          }
+          uint32_t x[1];
+          fetch_bytes<1>(arena, arena_len, off + l4, x);  // next header, length, fragment offset
+          if (nh == kNhFragment) {
+            ok = (bswap16(x[0] >> 16) & 0xFFF8u) == 0;
+            l4 += 8;
+          } else {
+            l4 += 8u * (((x[0] >> 8) & 0xFFu) + 1u);
+          }
+          nh = x[0] & 0xFFu;
+        }
+        ok = ok && nh == kTcpProtocol;
+      }
+      if (ok && l4 + kTcpHdrLen <= caplen && l4 + kTcpHdrLen <= kDecodeMaxHdr)
+        fetch_bytes<5>(arena, arena_len, off + l4, T);
+      if (v6) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          sa6[j] = A[j];
+          da6[j] = A[4 + j];
+        }
+      }
+    }
+  }
+  if (!ok || l4 + kTcpHdrLen > caplen || l4 + kTcpHdrLen > kDecodeMaxHdr) return false;
+  if (((T[3] >> 4) & 0xFu) < 5) return false;                 // tcp[12] >> 4: data offset
+  const uint32_t sport = bswap16(T[0] & 0xFFFFu);             // tcp[0..1]
+  const uint32_t dport = bswap16(T[0] >> 16);                 // tcp[2..3]
+  if (filter_port != 0 && sport != filter_port && dport != filter_port) return false;
+  const uint32_t seq = bswap32(T[1]), ack = bswap32(T[2]);    // tcp[4..7], tcp[8..11]
+  const uint32_t fb = T[3] >> 8;                              // tcp[13]: . . U A P R S F
+  const uint32_t window = bswap16(T[3] >> 16);                // tcp[14..15]
+  const uint32_t check = bswap16(T[4] & 0xFFFFu);             // tcp[16..17]
+  const uint32_t fl[6] = {(fb >> 5) & 1u, (fb >> 4) & 1u, (fb >> 3) & 1u,
+                          (fb >> 2) & 1u, (fb >> 1) & 1u, fb & 1u};
+  make_record(ts, v4, sa4, da4, sa6, da6, sport, dport, seq, ack, window, fl, check, R, K);
+  return true;
+}
+
+// ---------------------------------------------------------------------------
 // Decoupled look-back (one wave). Status word: bits 63:62 = 1 aggregate,
 // 2 inclusive prefix; bits 61:0 = value. Words are single 8-B agent-scope
 // stores polled by agent-scope loads (the data IS the flag).
@@ -260,8 +452,8 @@ __device__ __forceinline__ void lookback_publish(uint64_t* status, uint64_t tile
   st_agent(status + tile, (tile == 0 ? kFlagInc : kFlagAgg) | count);
 }
 
-template <int TILE>
-__device__ uint32_t tile_accept_count(const ParseArgs& a, uint64_t tile);
+template <int TILE, bool DECODE>
+__device__ __forceinline__ uint32_t tile_accept_count(const ParseArgs& a, uint64_t tile);
 
 // Resolves this tile's exclusive prefix (one wave) and publishes its inclusive
 // prefix. Tiles are blockIdx.x: no dispatch order is assumed. A predecessor
@@ -269,8 +461,10 @@ __device__ uint32_t tile_accept_count(const ParseArgs& a, uint64_t tile);
 // slow) has its aggregate recounted from the input by this wave (and published for
 // it), so the walk always terminates; results never depend on which block
 // publishes first.
-template <int TILE>
-__device__ uint64_t lookback_resolve(const ParseArgs& a, uint64_t tile, uint64_t count,
+// (always inlined, and tile_accept_count into it: as calls, the by-value kernel
+//  arguments they refer to would be copied to scratch at every kernel entry)
+template <int TILE, bool DECODE>
+__device__ __forceinline__ uint64_t lookback_resolve(const ParseArgs& a, uint64_t tile, uint64_t count,
                                     bool withhold) {
   const uint32_t lane = __lane_id();
   if (tile == 0) return 0;
@@ -291,7 +485,7 @@ __device__ uint64_t lookback_resolve(const ParseArgs& a, uint64_t tile, uint64_t
       if (!need) break;
       if (wall_clock64() - t0 > wait) {
         const uint32_t j = (uint32_t)__ffsll((unsigned long long)need) - 1;
-        const uint32_t cnt = tile_accept_count<TILE>(a, (uint64_t)(base - (int64_t)j));
+        const uint32_t cnt = tile_accept_count<TILE, DECODE>(a, (uint64_t)(base - (int64_t)j));
         if (lane == j) {
           // published on the predecessor's behalf (if it still has not): the other
           // successors waiting on it stop polling instead of each recounting it
@@ -335,6 +529,7 @@ __device__ __forceinline__ void lds_put_record(uint32_t* srec, uint32_t bo, cons
   }
 }
 
+template <bool DECODE>
 __device__ __forceinline__ bool parse_frame(const uint8_t* __restrict__ arena, uint64_t arena_len,
                                             uint64_t off, uint32_t caplen, uint64_t ts,
                                             uint32_t filter_port, uint32_t (&R)[19],
@@ -343,13 +538,15 @@ __device__ __forceinline__ bool parse_frame(const uint8_t* __restrict__ arena, u
   const uint32_t l[1] = {clamp_caplen(off, caplen, arena_len)};
   uint32_t w[1][24];
   load_windows<1>(arena, arena_len, o, l, w);
+  if (DECODE) return parse_decoded(arena, arena_len, off, l[0], ts, filter_port, w[0], R, K);
   return parse_window(arena, arena_len, off, l[0], ts, filter_port, w[0], R, K);
 }
 
 // Accepted frames of one tile, recomputed from the input by one wave (the
-// look-back's fallback when a predecessor has not published).
-template <int TILE>
-__device__ uint32_t tile_accept_count(const ParseArgs& a, uint64_t tile) {
+// look-back's fallback when a predecessor has not published), by the batch's own
+// accept predicate.
+template <int TILE, bool DECODE>
+__device__ __forceinline__ uint32_t tile_accept_count(const ParseArgs& a, uint64_t tile) {
   const uint32_t lane = __lane_id();
   uint32_t cnt = 0;
   for (int k = 0; k < TILE / 64; ++k) {
@@ -358,7 +555,7 @@ __device__ uint32_t tile_accept_count(const ParseArgs& a, uint64_t tile) {
     if (i < a.n) {
       uint32_t R[19];
       uint64_t K[5];
-      ok = parse_frame(a.arena, a.arena_len, a.offset[i], a.caplen[i], 0, a.filter_port, R, K);
+      ok = parse_frame<DECODE>(a.arena, a.arena_len, a.offset[i], a.caplen[i], 0, a.filter_port, R, K);
     }
     cnt += (uint32_t)__popcll(__ballot(ok));
   }
@@ -410,7 +607,7 @@ __device__ __forceinline__ void copy_out(uint8_t* __restrict__ out, uint64_t G0,
 // One tile of FPL x kBlock frames per block (tile = blockIdx.x). The tile's records
 // are staged in LDS at their compacted positions and stored by the whole block
 // after the look-back (a per-wave staging was slightly slower, round 2).
-template <int FPL, bool FLOWS>
+template <int FPL, bool FLOWS, bool DECODE>
 __global__ __launch_bounds__(kK1Block) void k_parse(ParseArgs a) {
   constexpr int TILE = kK1Block * FPL;
   constexpr int NW = kK1Block / 64;  // waves per tile
@@ -470,8 +667,10 @@ __global__ __launch_bounds__(kK1Block) void k_parse(ParseArgs a) {
     load_windows<FPL>(a.arena, a.arena_len, offv, lenc, W);
 #pragma unroll
     for (int f = 0; f < FPL; ++f)
-      acc[f] = parse_window(a.arena, a.arena_len, offv[f], lenc[f], tsv[f], a.filter_port, W[f],
-                            R[f], K[f]);
+      acc[f] = DECODE ? parse_decoded(a.arena, a.arena_len, offv[f], lenc[f], tsv[f],
+                                      a.filter_port, W[f], R[f], K[f])
+                      : parse_window(a.arena, a.arena_len, offv[f], lenc[f], tsv[f],
+                                     a.filter_port, W[f], R[f], K[f]);
   }
 #pragma unroll
   for (int f = 0; f < FPL; ++f) {
@@ -668,7 +867,7 @@ __global__ __launch_bounds__(kK1Block) void k_parse(ParseArgs a) {
   // (wave 0 resolving the look-back before its own probes instead — its inclusive
   //  prefix published a probe phase earlier — was 22 % slower, round 3)
   if (wave == 0) {
-    const uint64_t excl = lookback_resolve<TILE>(a, tile, total, withhold);
+    const uint64_t excl = lookback_resolve<TILE, DECODE>(a, tile, total, withhold);
     if (lane == 0) s_excl = excl;
   }
   __syncthreads();
@@ -2074,26 +2273,29 @@ hipError_t launch_table_init(FlowTable t, hipStream_t s) {
 }
 
 template <int FPL>
-static hipError_t launch_parse_fpl(const ParseArgs& a, bool flows, hipStream_t s) {
+static hipError_t launch_parse_fpl(const ParseArgs& a, bool flows, bool decode, hipStream_t s) {
   const dim3 grid((unsigned)a.ntiles);
-  if (flows) hipLaunchKernelGGL((k_parse<FPL, true>), grid, dim3(kK1Block), 0, s, a);
-  else hipLaunchKernelGGL((k_parse<FPL, false>), grid, dim3(kK1Block), 0, s, a);
+  if (decode) {
+    if (flows) hipLaunchKernelGGL((k_parse<FPL, true, true>), grid, dim3(kK1Block), 0, s, a);
+    else hipLaunchKernelGGL((k_parse<FPL, false, true>), grid, dim3(kK1Block), 0, s, a);
+  } else if (flows) hipLaunchKernelGGL((k_parse<FPL, true, false>), grid, dim3(kK1Block), 0, s, a);
+  else hipLaunchKernelGGL((k_parse<FPL, false, false>), grid, dim3(kK1Block), 0, s, a);
   return hipGetLastError();
 }
 
-hipError_t launch_parse(const ParseArgs& a, int fpl, bool flows, hipStream_t s) {
+hipError_t launch_parse(const ParseArgs& a, int fpl, bool flows, bool decode, hipStream_t s) {
   // (FPL 2 in every product context; 1 and 4: test tilings of the variants build)
   switch (fpl) {
-    case TCBEE_K1_FPL: return launch_parse_fpl<TCBEE_K1_FPL>(a, flows, s);
+    case TCBEE_K1_FPL: return launch_parse_fpl<TCBEE_K1_FPL>(a, flows, decode, s);
 #if TCBEE_VARIANTS
 #if TCBEE_K1_FPL != 1
-    case 1: return launch_parse_fpl<1>(a, flows, s);
+    case 1: return launch_parse_fpl<1>(a, flows, decode, s);
 #endif
 #if TCBEE_K1_FPL != 2
-    case 2: return launch_parse_fpl<2>(a, flows, s);
+    case 2: return launch_parse_fpl<2>(a, flows, decode, s);
 #endif
 #if TCBEE_K1_FPL != 4
-    case 4: return launch_parse_fpl<4>(a, flows, s);
+    case 4: return launch_parse_fpl<4>(a, flows, decode, s);
 #endif
 #endif
     default: return hipErrorInvalidValue;

@@ -583,6 +583,11 @@ int tcbee_pipe_run(tcbee_pipe* p, const tcbee_frames* in, const tcbee_cfg* cfg,
   if (!p || !in || !cfg || !out_n) return TCBEE_EINVAL;
   if (in->n && (!in->arena || !in->offset || !in->caplen || !in->ts_ns)) return TCBEE_EINVAL;
   if (out_cap && !out_rec74) return TCBEE_EINVAL;
+  // the decoded parse reads up to frame byte TCBEE_DECODE_MAX_HDR: a shorter header
+  // window (64 ships bytes [12, 76)) would cut what it may read
+  if ((cfg->flags & TCBEE_F_DECODE) && p->cfg.window && p->cfg.window < TCBEE_DECODE_MAX_HDR)
+    return TCBEE_EINVAL;
+  if (cfg->flags & ~(TCBEE_F_NO_FLOWS | TCBEE_F_DECODE)) return TCBEE_EINVAL;
   if (!p->cfg.window)
     for (uint64_t i = 0; i < in->n; ++i)
       if (in->caplen[i] > p->cfg.chunk_bytes) return TCBEE_ECAPACITY;

@@ -437,7 +437,7 @@ class OwnerExchange:
 def replay_pcap_sharded(pcap_path: str, out_prefix: str, direction: int = 0,
                         filter_port: int = 0, db_path: str | None = None, metrics: bool = True,
                         window: int = 64, chunk_frames: int = 1 << 20, threads: int = 8,
-                        group=None) -> dict:
+                        group=None, decode: bool = False) -> dict:
     """replay_pcap over the ranks of `group` (one process per GPU, collective): rank
     r streams the contiguous frames shard_range(n, r, world) of the capture (a
     zero-copy view of one mapping) through its own pinned pipeline into
@@ -449,6 +449,10 @@ def replay_pcap_sharded(pcap_path: str, out_prefix: str, direction: int = 0,
     counters, records and the slowest rank's seconds."""
     from . import _lib, host
     from .pipeline import Pipeline
+    if decode:
+        # the host partition (tcbee_flowhash_owner*) keys frames at the fixed offsets:
+        # a decoded flow could land on two GPUs (DESIGN.md section 7)
+        raise ValueError("replay_pcap_sharded: the decoded parse is single-GPU only")
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     name = "tc.tcp" if direction == _lib.DIR_EGRESS else "xdp.tcp"
     part = f"{out_prefix}{name}.part{rank}"

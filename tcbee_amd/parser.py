@@ -124,8 +124,11 @@ class PacketParser:
 
     # -- host-pointer path ---------------------------------------------------
     def parse(self, trace: Trace, filter_port: int = 0, direction: int = _lib.DIR_INGRESS,
-              flows: bool = True, out_cap: int | None = None) -> ParseResult:
-        """Synchronous: H2D frames, parse, D2H records (+ flow hash / id)."""
+              flows: bool = True, out_cap: int | None = None,
+              decode: bool = False) -> ParseResult:
+        """Synchronous: H2D frames, parse, D2H records (+ flow hash / id). decode: the
+        decoded parse (TCBEE_F_DECODE: VLAN tags, IHL, IPv6 extension headers, real
+        TCP flag bytes) instead of the reference's fixed offsets and zero flags."""
         n = trace.n
         cap = n if out_cap is None else int(out_cap)
         rec = np.empty((max(cap, 1), _lib.RECORD_BYTES), dtype=np.uint8)
@@ -134,7 +137,8 @@ class PacketParser:
         fr = _lib.Frames(trace.arena.ctypes.data if len(trace.arena) else 0, len(trace.arena),
                          trace.offset.ctypes.data, trace.caplen.ctypes.data,
                          trace.ts_ns.ctypes.data, n)
-        cfg = _lib.Cfg(filter_port, direction, 0, 0 if flows else _lib.F_NO_FLOWS)
+        cfg = _lib.Cfg(filter_port, direction, 0, (0 if flows else _lib.F_NO_FLOWS)
+                       | (_lib.F_DECODE if decode else 0))
         nout = C.c_uint64(0)
         ctr = _lib.Counters()
         _lib.check(self._L.tcbee_parse_batch(
@@ -150,8 +154,9 @@ class PacketParser:
                      counters=None, filter_port: int = 0,
                      direction: int = _lib.DIR_INGRESS, flows: bool = True,
                      stream: int | None = None, out_frame=None, defer_ids: bool = False,
-                     ids_stream: int | None = None) -> None:
+                     ids_stream: int | None = None, decode: bool = False) -> None:
         """Asynchronous parse of frames already in HBM (pointers or torch tensors).
+        decode: the decoded parse (TCBEE_F_DECODE), as in parse().
 
         out_n: device u64[1]; counters: device u64[4] (accumulated); out_frame:
         device u32[out_cap], the batch-local frame index of each record; defer_ids:
@@ -159,7 +164,8 @@ class PacketParser:
         ids_stream: run K3 there, beside the next batch's K1 (order readers of
         out_id / out_n / counters after that stream)."""
         fr = _lib.Frames(_ptr(arena), arena_len, _ptr(offset), _ptr(caplen), _ptr(ts_ns), n)
-        cfg = _lib.Cfg(filter_port, direction, 0, 0 if flows else _lib.F_NO_FLOWS)
+        cfg = _lib.Cfg(filter_port, direction, 0, (0 if flows else _lib.F_NO_FLOWS)
+                       | (_lib.F_DECODE if decode else 0))
         if out_frame is None and not defer_ids and not ids_stream:
             _lib.check(self._L.tcbee_parse_batch_device(
                 self._h, C.byref(fr), C.byref(cfg), _ptr(out_rec), C.c_uint64(out_cap),

@@ -28,11 +28,16 @@ class PipeResult:
 
 
 class Pipeline:
-    def __init__(self, device: int = 0, chunk_frames: int = 1 << 20, window: int = 64,
+    def __init__(self, device: int = 0, chunk_frames: int = 1 << 20, window: int | None = None,
                  depth: int = 3, threads: int = 8, chunk_bytes: int = 0,
-                 max_flows: int = 1 << 20, variants: bool = False):
+                 max_flows: int = 1 << 20, variants: bool = False, decode: bool = False):
         """variants=True: a pipe of the variants build (TCBEE_PIPE_* A/B settings
-        read from the environment; tests of those paths only)."""
+        read from the environment; tests of those paths only). decode: run()'s default
+        parse mode; window None = 64, or 128 for a decoded pipe (the decoded parse reads
+        up to frame byte 128: run(decode=True) on a shorter window is TCBEE_EINVAL)."""
+        if window is None:
+            window = 128 if decode else 64
+        self.decode = decode
         cfg = _lib.PipeCfg(chunk_frames, chunk_bytes, window, depth, threads, 0)
         h = C.c_void_p()
         self._L = _lib.lib(variants)
@@ -120,8 +125,9 @@ class Pipeline:
 
     def run(self, trace: Trace, filter_port: int = 0, direction: int = _lib.DIR_INGRESS,
             flows: bool = True, collect: bool = True, sink=None, out_rec=None,
-            out_id=None) -> PipeResult:
-        """Parse every frame of `trace`. collect: gather records (and flow ids) into
+            out_id=None, decode: bool | None = None) -> PipeResult:
+        """Parse every frame of `trace` (decode: the decoded parse, TCBEE_F_DECODE;
+        None = the pipe's default). collect: gather records (and flow ids) into
         arrays (or into the caller's out_rec [n,74] / out_id [n]). sink(rec, ids,
         first_record): called per chunk with numpy views valid during the call."""
         n = trace.n
@@ -149,7 +155,8 @@ class Pipeline:
         cb = _lib.PIPE_SINK_FN(_cb) if sink is not None else _lib.PIPE_SINK_FN()
         fr = _lib.Frames(_ptr(trace.arena) if len(trace.arena) else 0, len(trace.arena),
                          _ptr(trace.offset), _ptr(trace.caplen), _ptr(trace.ts_ns), n)
-        cfg = _lib.Cfg(filter_port, direction, 0, 0 if flows else _lib.F_NO_FLOWS)
+        cfg = _lib.Cfg(filter_port, direction, 0, (0 if flows else _lib.F_NO_FLOWS)
+                       | (_lib.F_DECODE if (self.decode if decode is None else decode) else 0))
         nout = C.c_uint64(0)
         ctr = _lib.Counters()
         rc = self._L.tcbee_pipe_run(self._h, C.byref(fr), C.byref(cfg), _ptr(rec), cap,
@@ -195,17 +202,19 @@ class Pipeline:
 
 def replay_pcap(pcap_path: str, out_prefix: str, direction: int = _lib.DIR_INGRESS,
                 filter_port: int = 0, db_path: str | None = None, metrics: bool = True,
-                device: int = 0, window: int = 64, chunk_frames: int = 1 << 20,
-                threads: int = 8) -> dict:
+                device: int = 0, window: int | None = None, chunk_frames: int = 1 << 20,
+                threads: int = 8, decode: bool = False) -> dict:
     """pcap -> GPU record path -> <out_prefix>xdp.tcp|tc.tcp (appended), optionally
     the tcbee-process SQLite database at db_path (records pre-grouped by the GPU's
-    flow ids), and <out_prefix>metrics.json. Returns counters and sink stats."""
+    flow ids), and <out_prefix>metrics.json. Returns counters and sink stats.
+    decode: the decoded parse (VLAN tags, IHL, IPv6 extension headers, real TCP
+    flags: the database then keeps the FLAG_* series); window None = 64, 128 decoded."""
     from . import host
     name = "tc.tcp" if direction == _lib.DIR_EGRESS else "xdp.tcp"
     out = {}
     with host.Pcap(pcap_path) as pc, Pipeline(device=device, window=window,
                                               chunk_frames=chunk_frames,
-                                              threads=threads) as pipe:
+                                              threads=threads, decode=decode) as pipe:
         tf = host.TcpFile(out_prefix + name)
         sk = host.Sink(db_path) if db_path else None
         try:
