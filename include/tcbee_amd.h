@@ -45,7 +45,10 @@ extern "C" {
 #define TCBEE_ABI_VERSION 5  /* 5: tcbee_gen_rss_load_range_device, TCBEE_RSS_INVALID,
                                 tcbee_ctx_create_ex, tcbee_pipe_register_output;
                               3: owner meta world+2 words, tcbee_status_raise_device;
-                                4: RSS indirection tables for the shard generator */
+                                4: RSS indirection tables for the shard generator.
+                              Still 5 with tcbee_group_scratch_bytes, tcbee_group_by_flow_device
+                              and tcbee_group_by_flow: additions only, nothing a caller of
+                              version 5 used has changed */
 
 /* ---- record / key layout constants (DESIGN.md "Data layout") ------------ */
 #define TCBEE_RECORD_BYTES   74  /* tcp_packet.rs:42 ENTRY_SIZE            */
@@ -409,6 +412,52 @@ int tcbee_ctx_status(tcbee_ctx* ctx);
  * block, 1 claims bucketed, 2 device atomics, 3 claim ranges per XCD column,
  * -1 none yet. Synchronous. */
 int tcbee_ctx_count_mode(tcbee_ctx* ctx, int* mode);
+
+/* ---- records grouped by flow (DESIGN.md "Grouping by flow") -----------------
+ * A batch's records regrouped flow-major on the device: a stable sort of the record
+ * indices by dense flow id, the bounds of every flow, and the per-flow series as
+ * columns. n = the record count (device call: *n_dev clamped to n_max, the parse's
+ * out_n_dev; n_dev NULL = n_max). key(i) = flow_id[i] when that is below n_ids, else
+ * n_ids: 0xFFFFFFFF (unclassified after TCBEE_EFLOWFULL) and every other id out of
+ * range form one trailing group.
+ *   perm       the stable sort of 0..n-1 by key: input indices rise inside a flow
+ *   flow_start [k] = records with key < k, k = 0..n_ids+1: flow k is the grouped
+ *              positions [flow_start[k], flow_start[k+1]), the unclassified group
+ *              [flow_start[n_ids], flow_start[n_ids+1]), flow_start[n_ids+1] = n
+ *   columns    at grouped position j, the little-endian field of record perm[j]
+ * Positions at or past n of every output are left as they are. Columns that are
+ * NULL cost nothing; with all of them NULL no record byte is read. */
+typedef struct tcbee_group_out {      /* device pointers; 64 bytes */
+    uint32_t* flow_start;  /* [n_ids + 2], required                               */
+    uint32_t* perm;        /* [n_max] or NULL: input index of the j-th grouped record */
+    uint64_t* ts_ns;       /* [n_max] or NULL: record bytes 0..7                  */
+    uint32_t* seq;         /* [n_max] or NULL: @52                                */
+    uint32_t* ack;         /* [n_max] or NULL: @56                                */
+    uint16_t* window;      /* [n_max] or NULL: @60                                */
+    uint16_t* checksum;    /* [n_max] or NULL: @68                                */
+    uint8_t*  flags;       /* [n_max] or NULL: bit 5..0 = record byte 62..67 != 0
+                              (urg, ack, psh, rst, syn, fin: TCP byte 13's low six
+                              bits in decoded mode, 0 in the default mode)        */
+} tcbee_group_out;
+/* Bytes of device scratch the device call needs (0 for arguments it would refuse);
+ * non-decreasing in n_max, independent of n_ids within its range. */
+uint64_t tcbee_group_scratch_bytes(uint64_t n_max, uint64_t n_ids);
+/* Asynchronous on `stream` (NULL = HIP's null stream, as tcbee_remap_ids_device);
+ * allocates nothing, does not synchronise, and no kernel of it waits on another
+ * workgroup. Limits, each TCBEE_EINVAL before any device work: 1 <= n_ids <= 2^24;
+ * n_max < 2^31; rec74_dev and scratch_dev 16-byte aligned; scratch_bytes >=
+ * tcbee_group_scratch_bytes(n_max, n_ids); rec74_dev, flow_id_dev, out,
+ * out->flow_start and scratch_dev not NULL. rec74_dev holds 74 n_max bytes (no byte
+ * past them is read), flow_id_dev n_max words at any 4-byte alignment. */
+int tcbee_group_by_flow_device(const uint8_t* rec74_dev, const uint32_t* flow_id_dev,
+                               const uint64_t* n_dev, uint64_t n_max, uint64_t n_ids,
+                               const tcbee_group_out* out,
+                               void* scratch_dev, uint64_t scratch_bytes, void* stream);
+/* The same from host arrays into host arrays (out_host holds host pointers):
+ * synchronous, with its own temporary device allocation and copies, like
+ * tcbee_parse_batch. */
+int tcbee_group_by_flow(int device, const uint8_t* rec74, const uint32_t* flow_id,
+                        uint64_t n, uint64_t n_ids, const tcbee_group_out* out_host);
 
 /* ---- measurement ------------------------------------------------------------
  * When enabled, every parse call records a HIP event pair around K1 (the parse

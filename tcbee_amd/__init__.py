@@ -8,6 +8,8 @@ classification of raw frames, emitting TCBee's 74-byte ``*.tcp`` records
 """
 from ._lib import (DIR_EGRESS, DIR_INGRESS, EXPORTED, F_DECODE, F_NO_FLOWS, KEY_BYTES,
                    LIB_PATH, RECORD_BYTES, TcbeeError, device_count, lib)
+from .group import (GROUP_TILE, FlowGroups, group_by_flow, group_by_flow_device,
+                    group_scratch_bytes)
 from .parser import (FLOW_DTYPE, PacketParser, ParseResult, flow_hash64, gen_frames_device,
                      gen_frames_index_device, gen_rss_load_device, gen_shard_index_device,
                      gen_shard_scratch_words)
@@ -20,5 +22,6 @@ __all__ = [
     "ParseResult", "flow_hash64", "gen_frames_device", "gen_frames_index_device",
     "gen_rss_load_device", "gen_shard_index_device", "gen_shard_scratch_words", "RSS_BUCKETS",
     "Trace", "rss_flows_per_rank", "rss_table", "splitmix64", "synth_flow_folds", "synth_index",
-    "synth_trace",
+    "synth_trace", "GROUP_TILE", "FlowGroups", "group_by_flow", "group_by_flow_device",
+    "group_scratch_bytes",
 ]

@@ -106,7 +106,14 @@ class PipeStats(C.Structure):
 # int (*)(void* user, const uint8_t* rec74, const uint32_t* flow_id, uint64_t n, uint64_t first)
 PIPE_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64)
 
+class GroupOut(C.Structure):
+    _fields_ = [("flow_start", C.c_void_p), ("perm", C.c_void_p), ("ts_ns", C.c_void_p),
+                ("seq", C.c_void_p), ("ack", C.c_void_p), ("window", C.c_void_p),
+                ("checksum", C.c_void_p), ("flags", C.c_void_p)]
+
+
 assert C.sizeof(Cfg) == 8 and C.sizeof(Frames) == 48 and C.sizeof(PipeCfg) == 32
+assert C.sizeof(GroupOut) == 64
 assert C.sizeof(Counters) == 32 and C.sizeof(FlowEntry) == 64 and C.sizeof(ParseEx) == 64
 
 # every symbol declared in include/tcbee_amd.h, with its ctypes signature
@@ -168,6 +175,12 @@ _SIGS = {
                                                    C.c_void_p]),
     "tcbee_remap_ids_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                          C.c_uint64, C.c_void_p]),
+    "tcbee_group_scratch_bytes": (C.c_uint64, [C.c_uint64, C.c_uint64]),
+    "tcbee_group_by_flow_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                             C.c_uint64, C.POINTER(GroupOut), C.c_void_p,
+                                             C.c_uint64, C.c_void_p]),
+    "tcbee_group_by_flow": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
+                                      C.POINTER(GroupOut)]),
     "tcbee_ctx_profile": (C.c_int, [C.c_void_p, C.c_int]),
     "tcbee_ctx_count_mode": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "tcbee_ctx_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double),

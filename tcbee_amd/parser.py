@@ -36,6 +36,11 @@ class ParseResult:
         """The bytes tcbee-record would have appended to xdp.tcp / tc.tcp."""
         return self.records.tobytes()
 
+    def group_by_flow(self, n_ids: int | None = None, device: int = 0):
+        """These records grouped by flow on the device (group.group_by_flow)."""
+        from .group import group_by_flow
+        return group_by_flow(self.records, self.flow_id, n_ids, device)
+
 
 def _ptr(x) -> int:
     """Raw address of a numpy array, torch tensor or int."""
