@@ -48,7 +48,9 @@ extern "C" {
                                 4: RSS indirection tables for the shard generator.
                               Still 5 with tcbee_group_scratch_bytes, tcbee_group_by_flow_device
                               and tcbee_group_by_flow: additions only, nothing a caller of
-                              version 5 used has changed */
+                              version 5 used has changed. Still 5 with tcbee_series_scratch_bytes,
+                              tcbee_flow_series_device and tcbee_flow_series, for the same
+                              reason */
 
 /* ---- record / key layout constants (DESIGN.md "Data layout") ------------ */
 #define TCBEE_RECORD_BYTES   74  /* tcp_packet.rs:42 ENTRY_SIZE            */
@@ -458,6 +460,68 @@ int tcbee_group_by_flow_device(const uint8_t* rec74_dev, const uint32_t* flow_id
  * tcbee_parse_batch. */
 int tcbee_group_by_flow(int device, const uint8_t* rec74, const uint32_t* flow_id,
                         uint64_t n, uint64_t n_ids, const tcbee_group_out* out_host);
+
+/* ---- per-flow series analysis (DESIGN.md "Per-flow series") ------------------
+ * Over the flow-major columns and flow_start[0 .. n_ids+1] of one batch, exactly as
+ * tcbee_group_by_flow_device writes them. n = min(flow_start[n_ids+1], n_max), read
+ * on the device. Segment k (0 <= k <= n_ids; k = n_ids is the trailing group, analysed
+ * like any other) is the positions [a, b) = [flow_start[k], flow_start[k+1]). Inside a
+ * segment, for x in {seq, ack}, all integer and exact:
+ *   d_x[a] = 0, d_x[j] = (int32_t)(x[j] - x[j-1])      serial-number arithmetic
+ *   rel_x[j] = sum of d_x[a..j] as int64     unwrapped, relative to the first record
+ *   hwm_x[j] = max of rel_x[a..j]            (>= 0)
+ *   below_x[j] = j > a and rel_x[j] < hwm_x[j-1]
+ *   repeat[j]  = j > a and seq[j] == seq[j-1] and ack[j] == ack[j-1]
+ *   gap[a] = 0, gap[j] = ts[j] - ts[j-1] when ts[j] >= ts[j-1], else 0
+ * The record carries no payload length, so below_seq is strict: a packet that starts
+ * exactly at the high-water mark (a retransmission of the newest segment) is not
+ * counted. The analysis covers one batch: a flow's state is not carried from one
+ * batch to the next, every batch starts each flow at rel = 0.
+ * Positions at or past n of the per-record outputs are left as they are; every row
+ * 0 .. n_ids of stats is written on every call. */
+typedef struct tcbee_flow_stats {     /* 72 bytes, little-endian */
+    uint64_t first_ts_ns, last_ts_ns; /* ts[a], ts[b-1]                               */
+    int64_t  seq_span, ack_span;      /* hwm_seq[b-1], hwm_ack[b-1]                   */
+    uint64_t max_gap_ns;              /* max of gap                                   */
+    uint32_t records;                 /* b - a                                        */
+    uint32_t n_seq_below, n_ack_below, n_repeat; /* counts of the three marks         */
+    uint32_t n_zero_window;           /* records with window == 0                     */
+    uint32_t win_min, win_max;        /* of window; an empty segment: 0xFFFF and 0    */
+    uint32_t flags_or;                /* OR of the flags column                       */
+} tcbee_flow_stats;                   /* an empty segment's row: 0 but win_min        */
+typedef struct tcbee_series_in {      /* device pointers; the columns 16-byte aligned */
+    const uint32_t* flow_start;       /* [n_ids + 2]                                  */
+    const uint64_t* ts_ns;            /* [n_max]; ts_ns, window and flags are read    */
+    const uint32_t* seq;              /* only for stats and may be NULL without it    */
+    const uint32_t* ack;
+    const uint16_t* window;
+    const uint8_t*  flags;
+} tcbee_series_in;
+typedef struct tcbee_series_out {     /* each NULL or: 16-byte aligned (stats: 8)     */
+    int64_t* seq_rel;                 /* [n_max] rel_seq                              */
+    int64_t* ack_rel;                 /* [n_max] rel_ack                              */
+    uint8_t* mark;                    /* [n_max] bit 0 below_seq, 1 below_ack, 2 repeat,
+                                         3 j == a (first of its flow in the batch)    */
+    tcbee_flow_stats* stats;          /* [n_ids + 1]                                  */
+} tcbee_series_out;
+/* Bytes of device scratch the device call needs (0 for arguments it would refuse);
+ * non-decreasing in both arguments. */
+uint64_t tcbee_series_scratch_bytes(uint64_t n_max, uint64_t n_ids);
+/* Asynchronous on `stream` (NULL = HIP's null stream); allocates nothing, does not
+ * synchronise, and no kernel of it waits on another workgroup. An output that is NULL
+ * costs neither a store nor the loads it alone needs. Each TCBEE_EINVAL before any
+ * device work: in, out, in->flow_start, in->seq, in->ack or scratch_dev NULL; ts_ns,
+ * window or flags NULL while stats is wanted; all four outputs NULL; n_ids outside
+ * 1 .. 2^24; n_max >= 2^31; a column, a per-record output or scratch_dev not 16-byte
+ * aligned (stats: 8, flow_start: 4); scratch_bytes below
+ * tcbee_series_scratch_bytes(n_max, n_ids). */
+int tcbee_flow_series_device(const tcbee_series_in* in, uint64_t n_max, uint64_t n_ids,
+                             const tcbee_series_out* out,
+                             void* scratch_dev, uint64_t scratch_bytes, void* stream);
+/* The same from host arrays into host arrays (both structs hold host pointers, any
+ * alignment): synchronous, with its own temporary device allocation and copies. */
+int tcbee_flow_series(int device, const tcbee_series_in* in_host, uint64_t n, uint64_t n_ids,
+                      const tcbee_series_out* out_host);
 
 /* ---- measurement ------------------------------------------------------------
  * When enabled, every parse call records a HIP event pair around K1 (the parse

@@ -13,6 +13,8 @@ from .group import (GROUP_TILE, FlowGroups, group_by_flow, group_by_flow_device,
 from .parser import (FLOW_DTYPE, PacketParser, ParseResult, flow_hash64, gen_frames_device,
                      gen_frames_index_device, gen_rss_load_device, gen_shard_index_device,
                      gen_shard_scratch_words)
+from .series import (SERIES_TILE, STATS_DTYPE, FlowSeries, flow_series, flow_series_device,
+                     series_scratch_bytes)
 from .trace import (RSS_BUCKETS, Trace, rss_flows_per_rank, rss_table, splitmix64, synth_flow_folds,
                     synth_index, synth_trace)
 
@@ -23,5 +25,6 @@ __all__ = [
     "gen_rss_load_device", "gen_shard_index_device", "gen_shard_scratch_words", "RSS_BUCKETS",
     "Trace", "rss_flows_per_rank", "rss_table", "splitmix64", "synth_flow_folds", "synth_index",
     "synth_trace", "GROUP_TILE", "FlowGroups", "group_by_flow", "group_by_flow_device",
-    "group_scratch_bytes",
+    "group_scratch_bytes", "SERIES_TILE", "STATS_DTYPE", "FlowSeries", "flow_series",
+    "flow_series_device", "series_scratch_bytes",
 ]

@@ -112,6 +112,17 @@ class GroupOut(C.Structure):
                 ("checksum", C.c_void_p), ("flags", C.c_void_p)]
 
 
+class SeriesIn(C.Structure):
+    _fields_ = [("flow_start", C.c_void_p), ("ts_ns", C.c_void_p), ("seq", C.c_void_p),
+                ("ack", C.c_void_p), ("window", C.c_void_p), ("flags", C.c_void_p)]
+
+
+class SeriesOut(C.Structure):
+    _fields_ = [("seq_rel", C.c_void_p), ("ack_rel", C.c_void_p), ("mark", C.c_void_p),
+                ("stats", C.c_void_p)]
+
+
+assert C.sizeof(SeriesIn) == 48 and C.sizeof(SeriesOut) == 32
 assert C.sizeof(Cfg) == 8 and C.sizeof(Frames) == 48 and C.sizeof(PipeCfg) == 32
 assert C.sizeof(GroupOut) == 64
 assert C.sizeof(Counters) == 32 and C.sizeof(FlowEntry) == 64 and C.sizeof(ParseEx) == 64
@@ -181,6 +192,12 @@ _SIGS = {
                                              C.c_uint64, C.c_void_p]),
     "tcbee_group_by_flow": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
                                       C.POINTER(GroupOut)]),
+    "tcbee_series_scratch_bytes": (C.c_uint64, [C.c_uint64, C.c_uint64]),
+    "tcbee_flow_series_device": (C.c_int, [C.POINTER(SeriesIn), C.c_uint64, C.c_uint64,
+                                           C.POINTER(SeriesOut), C.c_void_p, C.c_uint64,
+                                           C.c_void_p]),
+    "tcbee_flow_series": (C.c_int, [C.c_int, C.POINTER(SeriesIn), C.c_uint64, C.c_uint64,
+                                    C.POINTER(SeriesOut)]),
     "tcbee_ctx_profile": (C.c_int, [C.c_void_p, C.c_int]),
     "tcbee_ctx_count_mode": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "tcbee_ctx_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double),

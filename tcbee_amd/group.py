@@ -66,6 +66,11 @@ class FlowGroups:
         lo, hi = int(self.flow_start[k]), int(self.flow_start[k + 1])
         return {name: getattr(self, name)[lo:hi] for name in ("perm", *COLUMNS)}
 
+    def series(self, device: int = 0):
+        """The per-flow series analysis of these groups (series.flow_series)."""
+        from .series import flow_series
+        return flow_series(self, device)
+
 
 def group_by_flow(records, flow_id, n_ids: int | None = None, device: int = 0) -> FlowGroups:
     """Synchronous grouping of host arrays: records uint8 [n, 74], flow_id uint32 [n].
