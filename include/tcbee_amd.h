@@ -49,8 +49,10 @@ extern "C" {
                               Still 5 with tcbee_group_scratch_bytes, tcbee_group_by_flow_device
                               and tcbee_group_by_flow: additions only, nothing a caller of
                               version 5 used has changed. Still 5 with tcbee_series_scratch_bytes,
-                              tcbee_flow_series_device and tcbee_flow_series, for the same
-                              reason */
+                              tcbee_flow_series_device and tcbee_flow_series, and with
+                              tcbee_peers_scratch_bytes, tcbee_flow_peers_device,
+                              tcbee_peer_scratch_bytes and tcbee_flow_peer_series_device, for the
+                              same reason */
 
 /* ---- record / key layout constants (DESIGN.md "Data layout") ------------ */
 #define TCBEE_RECORD_BYTES   74  /* tcp_packet.rs:42 ENTRY_SIZE            */
@@ -522,6 +524,99 @@ int tcbee_flow_series_device(const tcbee_series_in* in, uint64_t n_max, uint64_t
  * alignment): synchronous, with its own temporary device allocation and copies. */
 int tcbee_flow_series(int device, const tcbee_series_in* in_host, uint64_t n, uint64_t n_ids,
                       const tcbee_series_out* out_host);
+
+/* ---- a flow joined with its reverse direction (DESIGN.md "Peer join") ----------
+ * Pairing. peer[k], k < n_ids, is the id p < n_ids, p != k, whose 40-byte tuple is
+ * entry k's with src_ip / dst_ip and sport / dport exchanged and the same protocol and
+ * padding bytes; TCBEE_NO_PEER when there is none (a tuple that is its own mirror
+ * included). peer[n_ids] = TCBEE_NO_PEER, the trailing group: n_ids + 1 words are
+ * written. Tuples are distinct, as the flow table guarantees; among duplicates any one
+ * match is taken. ent_dev is what tcbee_flow_export_device leaves on the device. */
+#define TCBEE_NO_PEER   0xFFFFFFFFu
+#define TCBEE_PEER_NONE INT64_MIN   /* una, wnd_edge, max_outstanding: no value */
+/* Bytes of device scratch (0 for n_ids outside 1 .. 2^24); non-decreasing. */
+uint64_t tcbee_peers_scratch_bytes(uint64_t n_ids);
+/* Asynchronous on `stream`, allocates nothing, does not synchronise; three kernels.
+ * TCBEE_EINVAL before any device work: a NULL pointer, n_ids outside 1 .. 2^24, ent_dev
+ * not 8-byte or peer_dev / scratch_dev not 4-byte aligned, scratch_bytes too small. */
+int tcbee_flow_peers_device(const tcbee_flow_entry* ent_dev, uint64_t n_ids, uint32_t* peer_dev,
+                            void* scratch_dev, uint64_t scratch_bytes, void* stream);
+
+/* The join, over one batch's flow-major columns as tcbee_group_by_flow_device and
+ * tcbee_flow_series_device write them. n = min(flow_start[n_ids+1], n_max), read on the
+ * device. Segment k = [a, b) with p = peer[k] and the peer's segment [c, d) =
+ * [flow_start[p], flow_start[p+1]). All integer and exact; for a position j of k:
+ *   q(j)  = the number of i in [c, d) with perm[i] < perm[j]: the peer's records
+ *           captured before j. perm rises inside a segment and is unique, so there are
+ *           no ties; timestamps play no part in the order.
+ *   A[j]  = what j acknowledges, in the peer's seq_rel frame: with q(j) > 0 and
+ *           m = c + q(j) - 1 (the peer's latest record before j)
+ *             A[j] = seq_rel[m] + (int32_t)(ack[j] - seq[m])    serial-number arithmetic
+ *           and with q(j) == 0, TCBEE_PEER_NONE: a record acknowledges nothing of a
+ *           peer not yet seen (this keeps the ack field of an opening SYN out without
+ *           the flags, which the default parse leaves 0).
+ *   H[j]  = max of A[a..j], per segment.
+ * Outputs, read against the peer's H:
+ *   una[j]      = H[c + q(j) - 1] when q(j) > 0, else TCBEE_PEER_NONE: the peer's
+ *                 cumulative ack, in k's own seq_rel frame, when j was captured
+ *   wnd_edge[j] = una[j] + window[c + q(j) - 1] when una[j] is a value, else
+ *                 TCBEE_PEER_NONE. The raw 16-bit window: the record carries no
+ *                 window-scale option, so a scaled connection's edge is too low.
+ *   rtt_ns[j]   : elig[j] = j + 1 < b and (int32_t)(seq[j+1] - seq[j]) > 0 and bit 0 of
+ *                 mark[j] clear (the flow's next record starts above this one, so this
+ *                 one advanced the sequence space — that stands in for the payload
+ *                 length the record lacks — and it is not below the high-water mark).
+ *                 f = the first i in [c + q(j), d) with H[i] > seq_rel[j]. A sample
+ *                 exists iff elig[j], f exists, and una[j] is no value or una[j] <=
+ *                 seq_rel[j] (not yet acknowledged when sent). Then rtt_ns[j] =
+ *                 ts[f] - ts[j], 0 if that is negative; without a sample UINT64_MAX.
+ *                 Known limit: Karn's rule is applied to the retransmission itself only;
+ *                 an original whose retransmission precedes the ack still yields a
+ *                 (short-counted) sample.
+ *   stats[k]    one row per segment 0 .. n_ids, written on every call.
+ * A segment without a peer, one whose peer's segment is empty and the trailing group get
+ * the no-value outputs per record and the identity row (its peer field still peer[k]).
+ * Positions at or past n of the per-record outputs are left as they are. */
+typedef struct tcbee_peer_stats {     /* 40 bytes, little-endian */
+    uint32_t peer;                    /* peer[k]                                      */
+    uint32_t rtt_samples;
+    uint64_t rtt_min_ns;              /* UINT64_MAX without a sample                  */
+    uint64_t rtt_max_ns;              /* 0 without a sample                           */
+    uint64_t rtt_sum_ns;              /* mod 2^64                                     */
+    int64_t  max_outstanding;         /* max of seq_rel[j] - una[j] over j with una[j] a
+                                         value; TCBEE_PEER_NONE if there is none      */
+} tcbee_peer_stats;
+typedef struct tcbee_peer_in {        /* device pointers; the columns 16-byte aligned */
+    const uint32_t* flow_start;       /* [n_ids + 2]                                  */
+    const uint32_t* peer;             /* [n_ids + 1]                                  */
+    const uint32_t* perm;             /* [n_max]                                      */
+    const uint64_t* ts_ns;            /* [n_max]; rtt_ns and stats only, else may be NULL */
+    const uint32_t* seq;
+    const uint32_t* ack;
+    const uint16_t* window;           /* wnd_edge only, else may be NULL              */
+    const int64_t*  seq_rel;          /* tcbee_series_out.seq_rel                     */
+    const uint8_t*  mark;             /* tcbee_series_out.mark; rtt_ns and stats only */
+} tcbee_peer_in;
+typedef struct tcbee_peer_out {       /* each NULL or: 16-byte aligned (stats: 8)     */
+    int64_t*  una;                    /* [n_max]                                      */
+    int64_t*  wnd_edge;               /* [n_max]                                      */
+    uint64_t* rtt_ns;                 /* [n_max]                                      */
+    tcbee_peer_stats* stats;          /* [n_ids + 1]                                  */
+} tcbee_peer_out;
+/* Bytes of device scratch (0 for arguments the call would refuse); non-decreasing in
+ * both arguments. */
+uint64_t tcbee_peer_scratch_bytes(uint64_t n_max, uint64_t n_ids);
+/* Asynchronous on `stream`; allocates nothing, does not synchronise, no kernel of it
+ * waits on another workgroup, and every launch is a kernel. An output that is NULL
+ * costs neither its store nor the loads and searches it alone needs. Each TCBEE_EINVAL
+ * before any device work: in, out, flow_start, peer, perm, seq, ack, seq_rel or
+ * scratch_dev NULL; all four outputs NULL; window NULL with wnd_edge wanted; ts_ns or
+ * mark NULL with rtt_ns or stats wanted; n_ids outside 1 .. 2^24; n_max >= 2^31; a
+ * column, a per-record output or scratch_dev not 16-byte aligned (stats: 8; flow_start
+ * and peer: 4); scratch_bytes below tcbee_peer_scratch_bytes(n_max, n_ids). */
+int tcbee_flow_peer_series_device(const tcbee_peer_in* in, uint64_t n_max, uint64_t n_ids,
+                                  const tcbee_peer_out* out,
+                                  void* scratch_dev, uint64_t scratch_bytes, void* stream);
 
 /* ---- measurement ------------------------------------------------------------
  * When enabled, every parse call records a HIP event pair around K1 (the parse

@@ -122,7 +122,19 @@ class SeriesOut(C.Structure):
                 ("stats", C.c_void_p)]
 
 
+class PeerIn(C.Structure):
+    _fields_ = [("flow_start", C.c_void_p), ("peer", C.c_void_p), ("perm", C.c_void_p),
+                ("ts_ns", C.c_void_p), ("seq", C.c_void_p), ("ack", C.c_void_p),
+                ("window", C.c_void_p), ("seq_rel", C.c_void_p), ("mark", C.c_void_p)]
+
+
+class PeerOut(C.Structure):
+    _fields_ = [("una", C.c_void_p), ("wnd_edge", C.c_void_p), ("rtt_ns", C.c_void_p),
+                ("stats", C.c_void_p)]
+
+
 assert C.sizeof(SeriesIn) == 48 and C.sizeof(SeriesOut) == 32
+assert C.sizeof(PeerIn) == 72 and C.sizeof(PeerOut) == 32
 assert C.sizeof(Cfg) == 8 and C.sizeof(Frames) == 48 and C.sizeof(PipeCfg) == 32
 assert C.sizeof(GroupOut) == 64
 assert C.sizeof(Counters) == 32 and C.sizeof(FlowEntry) == 64 and C.sizeof(ParseEx) == 64
@@ -198,6 +210,13 @@ _SIGS = {
                                            C.c_void_p]),
     "tcbee_flow_series": (C.c_int, [C.c_int, C.POINTER(SeriesIn), C.c_uint64, C.c_uint64,
                                     C.POINTER(SeriesOut)]),
+    "tcbee_peers_scratch_bytes": (C.c_uint64, [C.c_uint64]),
+    "tcbee_flow_peers_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                          C.c_uint64, C.c_void_p]),
+    "tcbee_peer_scratch_bytes": (C.c_uint64, [C.c_uint64, C.c_uint64]),
+    "tcbee_flow_peer_series_device": (C.c_int, [C.POINTER(PeerIn), C.c_uint64, C.c_uint64,
+                                                C.POINTER(PeerOut), C.c_void_p, C.c_uint64,
+                                                C.c_void_p]),
     "tcbee_ctx_profile": (C.c_int, [C.c_void_p, C.c_int]),
     "tcbee_ctx_count_mode": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "tcbee_ctx_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double),

@@ -72,6 +72,12 @@ class FlowSeries:
         return {"seq_rel": self.seq_rel[lo:hi], "ack_rel": self.ack_rel[lo:hi],
                 "mark": self.mark[lo:hi], "stats": self.stats[k]}
 
+    def peers(self, groups, flows, device: int = 0):
+        """Each flow joined with its reverse direction (peer.flow_peer_series): groups is
+        the FlowGroups this analysis was made from, flows the parser's flow table."""
+        from .peer import flow_peer_series
+        return flow_peer_series(groups, self, flows, device)
+
 
 def flow_series(groups, device: int = 0) -> FlowSeries:
     """Synchronous analysis of a FlowGroups (host arrays) on the device."""
